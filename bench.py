@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MLUPS of the D3Q19 BGK hot path on MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,11 +19,21 @@ each) overlapped with the interior update plus the residual all-reduce.  Populat
 resident in HBM before timing starts (generated on the device).
 
 Rank 0 prints ONE JSON line.  `value` = MLUPS over all ranks counting NX*NY*NZ box cells
-(SURVEY.md 8(d)); `roofline.achieved` = 152 B x fluid cells / average k_step
+(SURVEY.md 8(d)); `ms_per_step` = wall milliseconds per timed step (--steps of them);
+`roofline.achieved` = 152 B x fluid cells / average k_step
 duration from HIP events recorded on the kernel's own stream; `roofline.traffic` = the
-HBM bytes per launch rocprofv3 counted for the same kernel (profiles/pmc_traffic.json);
-`cpu_baseline` = the serial oracle (oracle/, a port of the reference algorithm) on one
-host core, N = 1 only.
+HBM bytes per launch rocprofv3 counted for the same kernel (profiles/pmc_traffic.json).
+
+A plain run does only that: set-up, warm-up, the timed steps, the line.  --full adds what takes
+runs of its own: `roofline.stream_probe*` (the device's best streaming copy in this run), and at
+N = 1 `secondary` (LDC 64^3, C2, the random-velocity start, the C5 lattice, C3, C4, the coronary
+tree) and `cpu_baseline` = the serial oracle (oracle/, a port of the reference algorithm) on one
+host core; --no-secondary and --no-cpu-baseline leave those two out of a --full run.
+
+--dump-outputs DIR writes, after the timed steps, what the last of them left for a caller
+(dump_outputs): the macroscopic fields lbm_get_macros returns and the residual state, as
+DIR/<name>.npy.  The cavity is generated on the device from constants, so equal arguments give
+equal inputs in every run and two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -45,6 +55,45 @@ torch = dist = lbm_amd = cases = ldist = None
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_PER_CELL = 152    # 19 fp32 loads + 19 fp32 stores per fluid cell update
+
+
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much over all ranks
+DUMP_SEED = 0
+
+
+def dump_outputs(lat, state: dict, out_dir: str, rank: int = 0, world: int = 1) -> dict:
+    """Write what the timed path's last step left for a caller to out_dir: rho, ux, uy, uz
+    (lat.macros(): fp32 [nz][ny][nx] of this rank's slab) and residual = [residual, velsum] of
+    lat.state() as float64.  Files are <name>.npy, or <name>.rank<r>.npy when world > 1; all ranks
+    together stay within DUMP_BYTES.  Fields that fit are written whole.  Of larger ones two
+    fixed parts are written, equal for equal shapes: <name>_lid.npy, the y-rows nearest the lid
+    [nz][rows][nx] (half of the field's share; the cavity is driven from y = ny - 2, and that is
+    where the flow is after a few steps), and <name>_sample.npy, the values at cell indices drawn
+    with numpy's default_rng(DUMP_SEED) from the whole slab, in ascending index order.  Returns
+    {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    ext = f".rank{rank}.npy" if world > 1 else ".npy"
+    names = ("rho", "ux", "uy", "uz")
+    fields = lat.macros()
+    nz, ny, nx = fields[0].shape
+    # 4 KiB set aside for the .npy headers and the residual file
+    share = (DUMP_BYTES // world - 4096) // (len(names) * 4)  # fp32 cells per field
+    out = {}
+    if fields[0].size <= share:
+        for k, a in zip(names, fields):
+            out[k + ext] = a
+    else:
+        rows = min(ny, share // 2 // (nz * nx))
+        pick = np.sort(np.random.default_rng(DUMP_SEED).integers(0, fields[0].size, share - rows * nz * nx))
+        for k, a in zip(names, fields):
+            if rows:
+                out[k + "_lid" + ext] = np.ascontiguousarray(a[:, ny - rows:, :])
+            out[k + "_sample" + ext] = a.reshape(-1)[pick]
+    out["residual" + ext] = np.array([state["residual"], state["velsum"]], np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k), a)
+    return {k: list(a.shape) for k, a in out.items()}
 
 
 def start_cpu_baseline(n: int = 512, steps: int = 1, quick: bool = False):
@@ -318,8 +367,12 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--n", type=int, default=512, help="per-GPU slab edge (nx = ny = nz_local)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fields and residual the last timed step left as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the stream probe, the secondary lattices and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lattices")
     return ap.parse_args(argv)
 
 
@@ -440,10 +493,10 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE {world}")
-    # the CPU baseline runs on its own host cores while the GPU is measured (N = 1 only); this
-    # process -- and every thread the HIP runtime starts from it -- keeps to the other cores
+    # --full: the CPU baseline runs on its own host cores while the GPU is measured (N = 1 only);
+    # this process -- and every thread the HIP runtime starts from it -- keeps to the other cores
     cpu_proc = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_proc = start_cpu_baseline()
         pin_away_from_samples()
     try:
@@ -491,6 +544,7 @@ def run(args, world, rank, local, n, nzg, cpu_proc):
     t1 = time.perf_counter()
     st = lat.stats()
     state = lat.state()
+    dumped = dump_outputs(lat, state, args.dump_outputs, rank, world) if args.dump_outputs else None
     elapsed = t1 - t0
     kern_ms = st["kernel_ms"]
     main_ms, main_n = st["step_kernel_ms"], max(1, st["step_kernel_launches"])
@@ -509,9 +563,9 @@ def run(args, world, rank, local, n, nzg, cpu_proc):
     setup = lat.setup_cost()
     lat.close()
 
-    # attainable streaming bandwidth of this device, same run (context for roofline.frac:
+    # --full: attainable streaming bandwidth of this device, same run (context for roofline.frac:
     # the 8 TB/s spec peak is not reached by any kernel)
-    probe_shapes = lbm_amd.probe_stream_shapes(local) if rank == 0 else None
+    probe_shapes = lbm_amd.probe_stream_shapes(local) if rank == 0 and args.full else None
     probe = max(probe_shapes.values()) if probe_shapes else None
 
     if rank != 0:
@@ -596,7 +650,9 @@ def run(args, world, rank, local, n, nzg, cpu_proc):
     }
     if world > 1:
         line["multi_gpu"] = multi_gpu_block(every, ms_step)
-    if world == 1 and not args.no_secondary:
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
+    if args.full and world == 1 and not args.no_secondary:
         line["secondary"] = {"ldc_64^3 (published config)": ldc_line(64, 2000, local, "ldc_64^3"),
                              "ldc_256^3 (C2)": c2_line(local),
                              f"ldc{n}_random_velocity_start": perturbed_mlups(n, 50, local),

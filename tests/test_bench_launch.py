@@ -1,7 +1,8 @@
 """bench.py's N > 1 plumbing on CPU: the self-launch (--gpus N without a launcher starts N
 ranks with the torchrun environment and returns the worst exit status) and the N > 1 report
 assembly (gather over gloo, the `multi_gpu` block, the communicator-size check), fed with
-fake per-rank statistics by two gloo ranks."""
+fake per-rank statistics by two gloo ranks; and the options of a plain run: --full is opt-in,
+--dump-outputs writes whole fields or, above its byte limit, the same fixed parts every time."""
 import importlib.util
 import json
 import os
@@ -37,6 +38,67 @@ def test_bench_import_loads_no_torch():
            "m=importlib.util.module_from_spec(s);s.loader.exec_module(m);print('torch' in sys.modules)"
     out = subprocess.run([sys.executable, "-c", code], cwd=REPO, capture_output=True, text=True, check=True)
     assert out.stdout.strip() == "False"
+
+
+def test_plain_run_is_the_default():
+    # --full (stream probe, secondary lattices, CPU baseline) and --dump-outputs are opt-in
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = b.parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+class _FakeLattice:
+    """macros() of a lattice of `shape` = [nz][ny][nx]: four fp32 fields, each cell its own index."""
+
+    def __init__(self, shape):
+        self.shape = shape
+
+    def macros(self):
+        import numpy as np
+        base = np.arange(int(np.prod(self.shape)), dtype=np.float32).reshape(self.shape)
+        return tuple(base + k for k in range(4))
+
+
+def _saved(d):
+    import numpy as np
+    return {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_dump_outputs_whole_fields(tmp_path):
+    import numpy as np
+    b = _bench()
+    lat = _FakeLattice((5, 6, 7))
+    files = b.dump_outputs(lat, {"residual": 0.25, "velsum": 3.0}, str(tmp_path / "a"))
+    got = _saved(tmp_path / "a")
+    assert sorted(got) == sorted(files) == ["residual.npy", "rho.npy", "ux.npy", "uy.npy", "uz.npy"]
+    for k, ref in zip(("rho", "ux", "uy", "uz"), lat.macros()):
+        assert got[k + ".npy"].dtype == np.float32 and np.array_equal(got[k + ".npy"], ref)
+    assert got["residual.npy"].dtype == np.float64 and got["residual.npy"].tolist() == [0.25, 3.0]
+    # a rank of two writes its own files
+    files = b.dump_outputs(lat, {"residual": 0.25, "velsum": 3.0}, str(tmp_path / "b"), rank=1, world=2)
+    assert sorted(files) == ["residual.rank1.npy", "rho.rank1.npy", "ux.rank1.npy", "uy.rank1.npy", "uz.rank1.npy"]
+
+
+def test_dump_outputs_large_fields_fixed_parts(tmp_path, monkeypatch):
+    import numpy as np
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_BYTES", 4096 + 4 * 4 * 1000)  # 1000 cells per field
+    lat = _FakeLattice((10, 12, 20))                            # 2400 cells: too large
+    for d in ("a", "b"):
+        b.dump_outputs(lat, {"residual": 1.0, "velsum": 2.0}, str(tmp_path / d))
+    got, again = _saved(tmp_path / "a"), _saved(tmp_path / "b")
+    assert sorted(got) == sorted(["residual.npy"] + [f"{k}_{p}.npy" for k in ("rho", "ux", "uy", "uz")
+                                                    for p in ("lid", "sample")])
+    assert all(np.array_equal(got[f], again[f]) for f in got)   # the same cells every time
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in got)
+    assert total <= 4096 + 4 * 4 * 1000
+    pick = np.sort(np.random.default_rng(b.DUMP_SEED).integers(0, 2400, 600))
+    for k, ref in zip(("rho", "ux", "uy", "uz"), lat.macros()):
+        # half the share as whole y-rows under the lid (500 // (10 * 20) = 2), the rest sampled
+        assert np.array_equal(got[k + "_lid.npy"], ref[:, 10:, :])
+        assert np.array_equal(got[k + "_sample.npy"], ref.reshape(-1)[pick])
 
 
 def test_self_launch_env_and_status(tmp_path):

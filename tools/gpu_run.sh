@@ -5,8 +5,8 @@
 # step that fails (a GPU fault, abort, segfault or time limit ends it: nothing more runs):
 #   tests      pytest -m gpu (TEST_PATHS="tests/a.py tests/b.py::test_x" narrows it) -> <tag>/tests.txt
 #   smoke      __graft_entry__.smoke()                              -> <tag>/smoke.txt
-#   bench      python bench.py $BENCH_ARGS (default: the driver's)  -> <tag>/bench.json
-#   spread     BENCH_RUNS fresh headline-only bench processes       -> <tag>/bench_spread.jsonl
+#   bench      python bench.py --full $BENCH_ARGS (every line)      -> <tag>/bench.json
+#   spread     BENCH_RUNS fresh plain (headline-only) bench runs    -> <tag>/bench_spread.jsonl
 #   prof       tools/gpu_profile.sh <tag>: kernel trace + FETCH_SIZE / WRITE_SIZE of the 512^3 bench
 #   lattices   tools/pmc_lattices.sh <tag> $LATTICES (default c3,c4,c4x4,coronary,ldc64,ldc256,c5)
 #   ab         tools/ab_lattices.py $AB_ARGS (AB_CASES selects lattices)  -> <tag>/ab.log
@@ -31,10 +31,10 @@ for s in ${steps//,/ }; do
   case $s in
     tests) run 900 "$out/tests.txt" python3 -u -m pytest ${TEST_PATHS:-tests} -m gpu -x -q --timeout 300 --timeout-method thread ;;
     smoke) run 300 "$out/smoke.txt" python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 900 "$out/bench.json" python3 -u bench.py ${BENCH_ARGS:-} ;;
+    bench) run 900 "$out/bench.json" python3 -u bench.py --full ${BENCH_ARGS:-} ;;
     spread)
       for i in $(seq 1 "${BENCH_RUNS:-3}"); do
-        run 300 "$out/bench_spread_$i.json" python3 -u bench.py --steps 50 --warmup 10 --no-secondary --no-cpu-baseline
+        run 300 "$out/bench_spread_$i.json" python3 -u bench.py --steps 50 --warmup 10
         tail -1 "$out/bench_spread_$i.json" >> "$out/bench_spread.jsonl"
       done ;;
     prof) run 1000 "$out/gpu_profile.log" bash tools/gpu_profile.sh "$tag" ;;
