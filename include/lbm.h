@@ -281,6 +281,35 @@ int lbm_get_nonfinite(lbm_ctx* ctx, int* k);
  * step kernels store no macros: the first read-out after stepping recomputes them on the
  * device from the last step's source buffer (the same pulls and sums, so the same bits). */
 int lbm_get_macros(lbm_ctx* ctx, float* rho, float* ux, float* uy, float* uz);
+/* Viscous stress tensor of the last step over the local planes z0 <= z < z1 (0 <= z0 < z1 <= nz,
+ * LBM_ERR_ARG otherwise), in lattice units: six raster arrays nx*ny*(z1-z0), x fastest (nullable);
+ * exactly 0.0f off-fluid, "fluid" being the cells lbm_get_macros fills.  It is the local moment
+ *   sigma = -(1 - 1/(2 tau)) * sum_q e_q e_q (f_q - feq_q)
+ * of the 19 populations the last step pulled -- from that step's source buffer with the pulls of
+ * lbm_get_macros (bounce-back and NEE slots, ghost planes of slabs) -- so it needs no velocity
+ * gradients.  Fixed arithmetic, fp64 from the 19 fp32 pulls d_q, left to right as written, no
+ * contraction:
+ *   r = d0+...+d18;  mx, my, mz: the momentum sums of lbm_get_macros' numerators
+ *   Pxx = d1+d2+d7+d8+d9+d10+d11+d12+d13+d14    Pxy = d7-d8-d9+d10
+ *   Pyy = d3+d4+d7+d8+d9+d10+d15+d16+d17+d18    Pxz = d11-d12-d13+d14
+ *   Pzz = d5+d6+d11+d12+d13+d14+d15+d16+d17+d18 Pyz = d15-d16-d17+d18
+ *   c = r/3.0;  k = 1.0 - 0.5/(double)tau
+ *   Nab = Pab - (ma*mb)/r;  Naa = (Paa - c) - (ma*ma)/r;  Sab = (-k)*Nab, returned as (float)Sab
+ * LBM_ERR_STATE before the first step; LBM_ERR_RCCL after a failed communicator.  The simulation
+ * state is untouched (a read-out waits for the streams and may restore wall and NEE slots, as
+ * lbm_get_macros does).  The context keeps no per-cell result arrays: the range is worked through
+ * in batches of planes with one transient device scratch of at most 256 MiB (one plane's outputs,
+ * 28 B per box cell, where a single plane needs more), freed before returning. */
+int lbm_get_stress(lbm_ctx* ctx, int z0, int z1, float* sxx, float* syy, float* szz, float* sxy, float* sxz,
+                   float* syz);
+/* Shear-stress magnitude of the same tensor, sqrt(1/2 s':s') with s' its deviatoric part:
+ *   p = ((Sxx+Syy)+Szz)/3.0;  Daa = Saa - p
+ *   J = 0.5*((Dxx*Dxx+Dyy*Dyy)+Dzz*Dzz) + ((Sxy*Sxy+Sxz*Sxz)+Syz*Syz);  shear = (float)sqrt(J)
+ * (fp64, from the unrounded Sab).  It needs no wall normal; next to a wall in simple shear it is
+ * the wall shear stress |s_tn|.  wall_only != 0: reported only at fluid cells with a code-1 wall
+ * cell among their 18 neighbours x - e_q (ghost planes of slabs count), 0 elsewhere.  *n_cells
+ * (nullable): the cells reported in the range.  Range, errors and memory as lbm_get_stress. */
+int lbm_get_shear(lbm_ctx* ctx, int z0, int z1, int wall_only, float* shear, int64_t* n_cells);
 /* Verification digest of the last step's fields, one uint64 per local plane: the wrapping sum
  * over the plane's fluid cells of a 64-bit hash of (global x, y, z, bits of rho, ux, uy, uz).
  * Independent of layout and slab decomposition, so the digests of z-slabs of a lattice equal

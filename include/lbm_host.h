@@ -72,6 +72,12 @@ int lbmh_write_vtk(const char* path, int case_kind, int nx, int ny, int nz, cons
  * x in [1, nx-2], y in [2, ny-3], z in [1, nz-2]; unstored cells print 0. */
 int lbmh_write_vtk_coronary(const char* path, int nx, int ny, int nz, const int8_t* geo, const float* rho,
                             const float* ux, const float* uy, const float* uz, float C_U, float CH, float C_rho);
+/* One scalar field over the whole box as legacy ASCII VTK (not a reference output; the stress
+ * read-outs of lbm.h): STRUCTURED_POINTS nx ny nz, spacing CH, origin 0, one section
+ * "SCALARS <name> float"; the values data[c] * scale (a float product) printed "%g", x fastest.
+ * Returns 0 or < 0 when the file cannot be written. */
+int lbmh_write_vtk_scalar(const char* path, int nx, int ny, int nz, const char* name, const float* data,
+                          float scale, float CH);
 /* calc_res (bifurcation.cu:1158-1175): long-double sum of the fp32 |u|^2 over code >= 4 in
  * the output region x in [1, nx-2], y in [2, ny-3], z in [1, nz-2] */
 long double lbmh_calc_res(int nx, int ny, int nz, const int8_t* geo, const float* ux, const float* uy,

@@ -2137,6 +2137,45 @@ int refresh_macros(lbm_ctx* c) {
 
 }  // namespace
 
+// The stress read-out's view of the last step's source buffer (lbm_stress.hip): the buffer,
+// per-cell arrays and wall links refresh_macros hands to k_moments, after the same waits and
+// restores.  The macros themselves are left as they are (stale or not).
+int lbm::stress_view(lbm_ctx* c, StressView* v) {
+  HIPCK(c, hipSetDevice(c->d.device));
+  RCK(wait_streams(c));
+  ConvState h{};
+  HIPCK(c, hipMemcpy(&h, c->conv, sizeof(ConvState), hipMemcpyDeviceToHost));
+  c->steps_done = h.k;
+  if (h.k == 0) {
+    c->err = "no step has run yet: the stress is a moment of the populations a step pulled";
+    return LBM_ERR_STATE;
+  }
+  if (!c->bb_pull()) RCK(prime_walls(c));
+  RCK(materialize_nee(c));
+  const bool consumer = c->bb_pull() && !c->bb_raw(h.k - 1);
+  *v = StressView{};
+  v->L = c->L;
+  v->src = c->buf[c->cur ^ 1];
+  v->compact = c->compact ? 1 : 0;
+  if (c->compact) {
+    v->type = c->ctype;
+    v->bb_links = consumer ? c->clinks : nullptr;
+    v->cmap = c->cmap; v->row_of = c->crow; v->rowrec = c->rowrec;
+    v->c_lo = c->whole.c_lo; v->c_hi = c->whole.c_hi;
+  } else {
+    v->type = c->type;
+    v->bb_links = consumer ? c->links : nullptr;
+  }
+  v->tau = c->d.tau;
+  v->device = c->d.device;
+  v->stream = c->s_comp;
+  return LBM_OK;
+}
+
+void lbm::stress_set_error(lbm_ctx* c, const char* what, hipError_t e) {
+  c->err = std::string(what) + ": " + hipGetErrorString(e);
+}
+
 extern "C" {
 
 int lbm_step(lbm_ctx* c, int nsteps, float* residual_hist, int* steps_done) {

@@ -377,6 +377,23 @@ int lbmh_write_vtk_coronary(const char* path, int nx, int ny, int nz, const int8
   return ofs.good() ? 0 : -2;
 }
 
+int lbmh_write_vtk_scalar(const char* path, int nx, int ny, int nz, const char* name, const float* data,
+                          float scale, float CH) {
+  if (!path || !name || !data || nx < 1 || ny < 1 || nz < 1) return -1;
+  std::FILE* fp = std::fopen(path, "w");
+  if (!fp) return -1;
+  const int64_t n = (int64_t)nx * ny * nz;
+  std::fprintf(fp, "# vtk DataFile Version 2.0\n%s\nASCII\nDATASET STRUCTURED_POINTS\n", name);
+  std::fprintf(fp, "DIMENSIONS %d %d %d\nSPACING %g %g %g\nORIGIN 0 0 0\n", nx, ny, nz, CH, CH, CH);
+  std::fprintf(fp, "POINT_DATA %lld\nSCALARS %s float\nLOOKUP_TABLE default\n", (long long)n, name);
+  for (int64_t c = 0; c < n; ++c) {
+    const float v = data[c] * scale;
+    std::fprintf(fp, (c + 1) % nx == 0 ? "%g\n" : "%g ", v);
+  }
+  const bool ok = std::ferror(fp) == 0;
+  return std::fclose(fp) == 0 && ok ? 0 : -2;
+}
+
 static long double calc_res_codes(int nx, int ny, int nz, const int8_t* geo, const float* ux, const float* uy,
                                   const float* uz, int lo, int hi) {
   const Box b{nx, ny, nz};

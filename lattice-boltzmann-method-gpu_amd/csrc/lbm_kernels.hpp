@@ -6,6 +6,8 @@
 
 #include <utility>
 
+struct lbm_ctx;  // include/lbm.h's opaque context (defined in lbm_ctx.hip)
+
 namespace lbm {
 
 // Cells are numbered linearly over a padded box, x fastest: c = x + y*pitch + zs*plane
@@ -266,6 +268,41 @@ hipError_t launch_moments(const float* src, const uint8_t* type, const uint32_t*
 hipError_t launch_moments_compact(const float* src, const uint8_t* type, const uint32_t* bb_links, const int* cmap,
                                   const int* row_of, const int4* rowrec, float* rho, float* ux, float* uy, float* uz,
                                   int64_t lo, int64_t hi, int swap, hipStream_t s);
+// Stress read-out (lbm_get_stress / lbm_get_shear, lbm_stress.hip).  stress_view (lbm_ctx.hip)
+// waits for the context's streams, restores what a read-out of the last step's source buffer
+// pulls (prime_walls, materialize_nee) and describes that buffer as the lazy macros address it;
+// it returns an LBM_* code (LBM_ERR_STATE before the first step, LBM_ERR_RCCL after a failed
+// communicator) and leaves the message in the context.
+struct StressView {
+  Layout L;
+  const float* src;          // the last step's source buffer (compact: the compact buffer)
+  const uint8_t* type;       // per cell of src's addressing (compact: per compact cell)
+  const uint32_t* bb_links;  // nullable: wall links of a consumer-side bounce-back step
+  int compact;               // 1: compact rows -- cells [c_lo, c_hi) through cmap / row_of / rowrec
+  const int* cmap;
+  const int* row_of;
+  const int4* rowrec;
+  int64_t c_lo, c_hi;
+  float tau;                 // lbm_desc.tau
+  int device;
+  hipStream_t stream;
+};
+int stress_view(::lbm_ctx* c, StressView* v);
+void stress_set_error(::lbm_ctx* c, const char* what, hipError_t e);
+// One launch over local planes [z0, z0 + nplanes): the six stress components and the shear of
+// every fluid cell into raster arrays of the batch (x fastest, index ((z - z0) * ny + y) * nx + x;
+// nullable, only the given ones are written; cells the kernel skips are left as they are).
+// wall_only: the shear only at fluid cells with a wall among their 18 neighbours (kWallAdj).
+// counts (device, stress_blocks(v, nplanes) slots): every block of the launch stores the number of
+// cells it reported into its own slot; the caller adds them.
+struct StressOut {
+  float* s[6];  // xx, yy, zz, xy, xz, yz
+  float* shear;
+  unsigned* counts;
+};
+int stress_blocks(const StressView& v, int nplanes);
+hipError_t launch_stress(const StressView& v, int z0, int nplanes, int wall_only, const StressOut& o);
+
 // per local plane digest of the fluid (rho, u) bits keyed by global coordinates (lbm_field_digest);
 // out[nz] must be zeroed
 hipError_t launch_digest(const uint8_t* type, const float* rho, const float* ux, const float* uy, const float* uz,

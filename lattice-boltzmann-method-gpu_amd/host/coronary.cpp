@@ -7,6 +7,9 @@
 // Overrides: --geo PATH --repeat N --time-save N --out DIR --device N
 //            --nx N --ny N --nz N --ends "axis,plane,lo0,hi0,lo1,hi1,passes;..." (another box and its
 //            own end table, lbmh_end; the reference's table needs a box of at least 274 x 201 x 206)
+//            --stress: at every save step also wss_<i>.vtk, the wall shear stress (lbm_get_shear at
+//            the wall-adjacent fluid cells, 0 elsewhere) in pascals: lattice units x C_rho * C_U^2,
+//            outputSave's C_pre in float, over the whole box
 #include "driver_common.hpp"
 
 #include <sstream>
@@ -85,6 +88,8 @@ int main(int argc, char** argv) {
   drv::check(lbm_init_equilibrium(ctx, LBM_INIT_EXPANDED, f.rho.data(), f.ux.data(), f.uy.data(), f.uz.data()), ctx,
              "lbm_init_equilibrium");
   // host copies start as initialize()'s fields (calc_res at i = 0 reads them: coronary.cu:1114)
+  const bool want_stress = args.has("--stress");
+  std::vector<float> wss(want_stress ? n : 0);
   drv::Timer timer;
   float residual = 0.0f;
   long double sum1 = 0.0L, sum2 = 0.0L;
@@ -105,6 +110,14 @@ int main(int argc, char** argv) {
       std::printf("ITERATION # %d, collapse time: %g ms, residual:%g\n", last, milli, residual);
       lbmh_write_vtk_coronary((out + "/coronary_" + std::to_string(last) + ".vtk").c_str(), NX, NY, NZ, geo.data(),
                               f.rho.data(), f.ux.data(), f.uy.data(), f.uz.data(), C_U, CH, C_rho);
+      if (want_stress) {  // the wall shear stress of this step, in pascals
+        drv::check(lbm_get_shear(ctx, 0, NZ, 1, wss.data(), nullptr), ctx, "lbm_get_shear");
+        if (lbmh_write_vtk_scalar((out + "/wss_" + std::to_string(last) + ".vtk").c_str(), NX, NY, NZ, "WSS", wss.data(),
+                                  C_rho * C_U * C_U, CH) != 0) {
+          std::fprintf(stderr, "cannot write %s/wss_%d.vtk\n", out.c_str(), last);
+          return 1;
+        }
+      }
     }
   }
   const float milli = timer.ms();

@@ -90,12 +90,13 @@ LBM_SYMBOLS = [
     "lbm_get_nee_path", "lbm_get_setup_cost",
     "lbm_get_layout", "lbm_get_launch_shape", "lbm_buffer_placement", "lbm_checkpoint_save", "lbm_checkpoint_load",
     "lbm_rccl_unique_id", "lbm_attach_rccl", "lbm_comm_info", "lbm_debug_fail_next_wait", "lbm_debug_poison_walls",
-    "lbm_group_step", "lbm_probe_stream", "lbm_probe_stream_shapes",
+    "lbm_group_step", "lbm_probe_stream", "lbm_probe_stream_shapes", "lbm_get_stress", "lbm_get_shear",
 ]
 HOST_SYMBOLS = [
     "lbmh_geo_ldc", "lbmh_geo_poiseuille", "lbmh_geo_mask", "lbmh_read_geo_txt", "lbmh_read_bc_txt",
     "lbmh_index_transform", "lbmh_poiseuille_profile", "lbmh_initial_fields", "lbmh_write_vtk", "lbmh_calc_res",
     "lbmh_read_geo_txt_zxy", "lbmh_geo_ends", "lbmh_coronary_ends", "lbmh_write_vtk_coronary", "lbmh_calc_res_fluid",
+    "lbmh_write_vtk_scalar",
 ]
 
 
@@ -145,6 +146,8 @@ def host_lib() -> C.CDLL:
             "lbmh_coronary_ends": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(lbmh_end)]),
             "lbmh_write_vtk_coronary": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, i8p, f32p, f32p, f32p, f32p,
                                                   C.c_float, C.c_float, C.c_float]),
+            "lbmh_write_vtk_scalar": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, f32p, C.c_float,
+                                                C.c_float]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -177,6 +180,8 @@ def lbm_lib() -> C.CDLL:
             "lbm_get_state": (C.c_int, [P, ip, ip, ip, f32p, f64p]),
             "lbm_get_macros": (C.c_int, [P, f32p, f32p, f32p, f32p]),
             "lbm_get_f": (C.c_int, [P, f32p]),
+            "lbm_get_stress": (C.c_int, [P, C.c_int, C.c_int, f32p, f32p, f32p, f32p, f32p, f32p]),
+            "lbm_get_shear": (C.c_int, [P, C.c_int, C.c_int, C.c_int, f32p, i64p]),
             "lbm_field_digest": (C.c_int, [P, C.POINTER(C.c_uint64)]),
             "lbm_get_geo": (C.c_int, [P, C.POINTER(C.c_int8)]),
             "lbm_get_counts": (C.c_int, [P, i64p, i64p, f64p]),
@@ -214,13 +219,14 @@ def lbm_lib() -> C.CDLL:
 
 def kernel_fingerprint() -> str:
     """16 hex digits identifying the code of liblbm's kernels and launch logic: sha256 of
-    csrc/lbm_kernels.hip, lbm_kernels.hpp, lbm_d3q19.hpp and lbm_ctx.hip with // comments and
-    whitespace removed.  Profiles record it (tools/pmc_*.py) so that bench.py reports measured
-    HBM traffic only next to the kernels it was measured on."""
+    csrc/lbm_kernels.hip, lbm_kernels.hpp, lbm_d3q19.hpp, lbm_ctx.hip and lbm_pull.hpp (the step's
+    addressing and one-cell pulls) with // comments and whitespace removed.  Profiles record it
+    (tools/pmc_*.py) so that bench.py reports measured HBM traffic only next to the kernels it
+    was measured on.  lbm_stress.hip (read-outs only) is not part of it."""
     import hashlib
     import re
     h = hashlib.sha256()
-    for name in ("lbm_kernels.hip", "lbm_kernels.hpp", "lbm_d3q19.hpp", "lbm_ctx.hip"):
+    for name in ("lbm_kernels.hip", "lbm_kernels.hpp", "lbm_d3q19.hpp", "lbm_ctx.hip", "lbm_pull.hpp"):
         text = open(os.path.join(ROOT, "csrc", name)).read()
         text = re.sub(r"//[^\n]*", "", text)
         h.update(re.sub(r"\s+", "", text).encode())
@@ -325,6 +331,15 @@ def write_vtk_coronary(path: str, geo: np.ndarray, rho, ux, uy, uz, C_U: float =
     arrs = [np.ascontiguousarray(a, np.float32) for a in (rho, ux, uy, uz)]
     rc = host_lib().lbmh_write_vtk_coronary(path.encode(), nx, ny, nz, _ptr(g, C.c_int8),
                                             *[_ptr(a, C.c_float) for a in arrs], C_U, CH, C_rho)
+    if rc != 0:
+        raise LbmError(f"cannot write {path}")
+
+
+def write_vtk_scalar(path: str, name: str, data: np.ndarray, scale: float = 1.0, CH: float = 1.0) -> None:
+    """One float32 field [nz][ny][nx] times scale as legacy ASCII VTK (lbmh_write_vtk_scalar)."""
+    a = np.ascontiguousarray(data, np.float32)
+    nz, ny, nx = a.shape
+    rc = host_lib().lbmh_write_vtk_scalar(os.fsencode(path), nx, ny, nz, name.encode(), _ptr(a, C.c_float), scale, CH)
     if rc != 0:
         raise LbmError(f"cannot write {path}")
 
@@ -537,6 +552,26 @@ class Lattice:
         out = [np.zeros(self.shape, np.float32) for _ in range(4)]
         self._ck(lbm_lib().lbm_get_macros(self.h, *[_ptr(a, C.c_float) for a in out]), "lbm_get_macros")
         return tuple(out)
+
+    def stress(self, z0: int = 0, z1: int | None = None) -> np.ndarray:
+        """The last step's viscous stress tensor over local planes [z0, z1) (lbm_get_stress), lattice
+        units: float32 (6, z1 - z0, ny, nx) in the order xx, yy, zz, xy, xz, yz; 0 off-fluid."""
+        z1 = self.shape[0] if z1 is None else z1
+        out = np.zeros((6, max(z1 - z0, 0)) + self.shape[1:], np.float32)
+        self._ck(lbm_lib().lbm_get_stress(self.h, z0, z1, *[_ptr(out[k], C.c_float) for k in range(6)]),
+                 "lbm_get_stress")
+        return out
+
+    def shear(self, z0: int = 0, z1: int | None = None, wall_only: bool = True):
+        """(shear, n_cells): the shear-stress magnitude sqrt(1/2 s':s') of that tensor over local planes
+        [z0, z1) (lbm_get_shear), float32 (z1 - z0, ny, nx); wall_only: only at fluid cells with a wall
+        among their 18 neighbours -- the wall shear stress -- and 0 elsewhere.  n_cells: cells reported."""
+        z1 = self.shape[0] if z1 is None else z1
+        out = np.zeros((max(z1 - z0, 0),) + self.shape[1:], np.float32)
+        n = C.c_int64()
+        self._ck(lbm_lib().lbm_get_shear(self.h, z0, z1, 1 if wall_only else 0, _ptr(out, C.c_float), C.byref(n)),
+                 "lbm_get_shear")
+        return out, n.value
 
     def digest(self) -> np.ndarray:
         """Per-plane uint64 digest of the fluid (rho, u) bits keyed by global coordinates
