@@ -209,8 +209,10 @@ typedef enum {
                                    recorded and their own post-collision slots (round 5's default);
                                    2 NEE records -- a chunk wave computes them after its relaxation
                                    into a 32-B record per cell, and the next step's wave puts them
-                                   into its pulls (chunk lists of the dense box with at most 8 such
-                                   cells per chunk; otherwise as 3) */
+                                   into its pulls (chunk lists of the dense box without lane masks --
+                                   contiguous, or sparse with no partly idle chunk: a pipe whose
+                                   rows are whole chunks -- and at most 8 such cells per chunk;
+                                   otherwise as 3) */
   LBM_TUNE_XCD_RUN = 13,        /* order of the step kernel's chunk workgroups over the 8 XCDs: 0
                                    (default) runs of eight (L = 4) for 4-cell chunk lists whose rows
                                    run along y (the pipe), runs of four (L = 3) for compact one-cell

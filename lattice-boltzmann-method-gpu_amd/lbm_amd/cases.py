@@ -96,6 +96,67 @@ def duct_generic(nx: int, ny: int, nz: int, u_in: float = 0.05, u_out: float = 0
     return g, bcs, (rho, ux, uy, uz)
 
 
+BOX_U = (0.004, -0.003, 0.002)                       # tangential components stay non-zero
+BOX_U_NORMAL = (0.03, 0.02, 0.015, 0.01, 0.012, 0.018)  # per face PX, NX, PY, NY, PZ, NZ
+BOX_CODES = (2, 3, 5, 6, 7, 8)                        # code of face 0..5
+
+
+def box_patches(nx: int, ny: int, nz: int):
+    """box_generic's six boundary patches as [z, y, x] index tuples, face 0..5."""
+    return [
+        (slice(2, nz - 2), slice(2, ny - 2), 1),                 # PX: the whole cross-section
+        (slice(2, nz // 2 + 1), slice(3, ny - 4), nx - 2),       # NX
+        (slice(3, nz - 3), 1, slice(4, nx - 3)),                 # PY
+        (slice(2, nz - 2), ny - 2, slice(2, nx // 2)),           # NY
+        (1, slice(2, ny - 2), slice(3, nx - 4)),                 # PZ
+        (nz - 2, slice(3, ny - 3), slice(nx // 2, nx - 2)),      # NZ
+    ]
+
+
+def box_table(face: int, nx: int, ny: int, nz: int) -> np.ndarray:
+    """u_normal_table of box_generic's face: on the face's raster [j][i] (x faces [nz][ny], y faces
+    [nz][nx], z faces [ny][nx]) u_n * (1 + 0.3 i/ni - 0.2 j/nj), float32 -- asymmetric in both
+    indices with ni != nj, so a transposed, flipped or mis-strided lookup changes bits."""
+    nj, ni = ((nz, ny), (nz, nx), (ny, nx))[face >> 1]
+    j, i = np.meshgrid(np.arange(nj, dtype=np.float64), np.arange(ni, dtype=np.float64), indexing="ij")
+    return (BOX_U_NORMAL[face] * (1.0 + 0.3 * i / ni - 0.2 * j / nj)).astype(np.float32)
+
+
+def box_generic(nx: int, ny: int, nz: int, cfg: int = 0):
+    """A closed box with one NEE patch in each of its six walls, for LBM_CASE_GENERIC: wall (1) on
+    [1:-1] and fluid (4) on [2:-2] along every axis; codes 2, 3, 5, 6, 7, 8 on faces PX, NX, PY, NY,
+    PZ, NZ (box_patches).  The kind of face f in configuration cfg (0..2) is (f + cfg) % 3, so the
+    three configurations hold each of the 18 (face, kind) pairs once.  u_bc = BOX_U with the
+    component along the face's axis replaced by BOX_U_NORMAL[f]; rho_bc = 1 + 0.01 on even faces,
+    1 - 0.01 on odd ones; every code carries a table (box_table), pressure codes included (where it
+    must be ignored).  The patches touch (PX meets NY, NY meets PZ), so some fluid cells have NEE
+    neighbours on two faces.  Returns (geo, bcs, fields) like duct_generic: rho = 1 everywhere and
+    u = 0, but u = u_bc (its table value along the face's axis) on the cells of velocity codes --
+    the state the reference's initialize() and the oracle start a generic lattice from, which the
+    first step pulls from the boundary cells as it is."""
+    g = np.zeros((nz, ny, nx), np.int8)
+    g[1:nz - 1, 1:ny - 1, 1:nx - 1] = 1
+    g[2:nz - 2, 2:ny - 2, 2:nx - 2] = 4
+    bcs = []
+    for face, (code, patch) in enumerate(zip(BOX_CODES, box_patches(nx, ny, nz))):
+        g[patch] = code
+        u = list(BOX_U)
+        u[face >> 1] = BOX_U_NORMAL[face]
+        bcs.append({"code": code, "face": face, "kind": (face + cfg) % 3, "rho": 1.0 + (0.01 if face % 2 == 0 else -0.01),
+                    "u": tuple(u), "table": box_table(face, nx, ny, nz)})
+    rho = np.ones(g.shape, np.float32)
+    vel = [np.zeros(g.shape, np.float32) for _ in range(3)]
+    for b in bcs:
+        if b["kind"] == 2:  # pressure: u_bc is the fluid neighbour's
+            continue
+        axis = b["face"] >> 1
+        z, y, x = np.nonzero(g == b["code"])
+        for k in range(3):
+            vel[k][z, y, x] = np.float32(b["u"][k])
+        vel[axis][z, y, x] = b["table"][((z, y), (z, x), (y, x))[axis]]
+    return g, bcs, (rho, *vel)
+
+
 def generic(geo, bcs, fields, tau: float = 0.6, device: int = 0):
     """A LBM_CASE_GENERIC lattice initialised at the equilibrium of `fields` (expanded form)."""
     from . import LBM_CASE_GENERIC

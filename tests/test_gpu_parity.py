@@ -452,8 +452,9 @@ def test_poiseuille_nee_paths_bitwise(gpu, oracle, knob, nee_fix, shape):
     """The pipe along y with four cells per lane: its chunk waves collide the NEE-adjacent cells
     (nee_chunks), and the NEE values come from NEE blocks that re-pull and re-collide those cells
     (LBM_TUNE_NEE_FIX 1, the default), from k_nee_fix after the step launch (3), or from NEE records
-    (2, where every chunk holds at most 8 NEE-adjacent cells: rows of 300 and 512 cells; the 40-
-    and 70-cell rows fall back to k_nee_fix).  All bit for bit against the oracle, populations
+    (2, where the chunk list carries no lane masks and every chunk holds at most 8 NEE-adjacent
+    cells: the rows of 512 cells, two whole chunks each; the 40-, 70- and 300-cell rows fall back
+    to k_nee_fix, see test_gpu_tau.py).  All bit for bit against the oracle, populations
     included (the read-outs put the records' values into the NEE cells' slots), through the
     convergence-free loop and a convergence-controlled one (no-op steps after the stop write no
     record and launch no k_nee_fix)."""

@@ -28,11 +28,15 @@ def _same(a, b, what):
     assert bad == 0, f"{what}: {bad} of {np.asarray(a).size} values differ in their bits"
 
 
-def _make(case):
-    """(lattice, geo, fluid code, tau, oracle factory) of a named case."""
+def _make(case, tau=None):
+    """(lattice, geo, fluid code, tau, oracle factory) of a named case (tau: the box's, default 0.6)."""
     import orc
     from lbm_amd import cases
     kind, shape = case
+    if kind == "box":
+        tau = 0.6 if tau is None else tau
+        geo, bcs, fields = cases.box_generic(*shape, 0)
+        return cases.generic(geo, bcs, fields, tau=tau), geo, 4, tau, (lambda: orc.Oracle(orc.GENERIC, geo, tau, bcs=bcs))
     if kind == "ldc":
         lat, geo = cases.ldc(*shape)
         return lat, geo, 3, 0.55, (lambda: orc.Oracle(orc.LDC, geo, 0.55, ldc_order=orc.TWO_PHASE))
@@ -47,10 +51,10 @@ def _make(case):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(case, k):
-    """stress_ref of the oracle's populations after k - 1 steps: computed once per (case, k) and
+def _reference(case, k, tau=None):
+    """stress_ref of the oracle's populations after k - 1 steps: computed once per (case, k, tau) and
     shared by every layout (read-only)."""
-    lat, geo, fluid, tau, make_oracle = _make(case)
+    lat, geo, fluid, tau, make_oracle = _make(case, tau)
     lat.close()
     o = make_oracle()
     if k > 1:
@@ -76,7 +80,7 @@ def _check(lat, ref, what, zsl=slice(None)):
 
 CASES = [(("ldc", (16, 16, 16)), 1), (("ldc", (16, 16, 16)), 20), (("ldc", (37, 29, 23)), 17),
          (("poiseuille", (20, 16, 20)), 1), (("poiseuille", (20, 16, 20)), 30), (("poiseuille", (13, 11, 7)), 17),
-         (("duct", (24, 14, 12)), 25), (("bifurcation", ()), 30)]
+         (("duct", (24, 14, 12)), 25), (("bifurcation", ()), 30), (("box", (21, 18, 15)), 11)]
 
 
 @pytest.mark.parametrize("case,k", CASES, ids=[f"{c[0]}{'x'.join(map(str, c[1]))}-k{k}" for c, k in CASES])
@@ -89,6 +93,29 @@ def test_stress_bitwise(gpu, oracle, case, k, cells_per_lane, row_axis):
     lat = _make(case)[0]
     lat.step(k, history=False)
     _check(lat, ref, f"{case} k={k}")
+    lat.close()
+
+
+@pytest.mark.parametrize("tau", [0.5, 1.0, 17.0])
+def test_stress_tau(gpu, oracle, tau):
+    """k = 1 - 0.5 / tau across tau on the six-face box (cfg 0) at step 11: tau 1.0 (k = 0.5) and
+    17.0 bit for bit like test_stress_bitwise; at tau = 0.5 k = 0 and every component is a zero
+    whose sign is that of the restatement's (-k) * N -- 7,841 negative zeros among the 6 x 2,618
+    fluid values, 502 cells at the wall -- so the bits, signs included, still have to match."""
+    case, k = ("box", (21, 18, 15)), 11
+    ref = _reference(case, k, tau)
+    assert (ref["n_fluid"], ref["n_wall"]) == (2618, 502)
+    fl = ref["fluid"]
+    if tau == 0.5:
+        assert not ref["stress"].any() and not ref["shear"].any()
+        assert 0 < np.count_nonzero(np.signbit(ref["stress"][:, fl])) < 6 * ref["n_fluid"]
+    else:
+        assert np.any(ref["stress"] != 0) and np.any(ref["shear_wall"] != 0)
+    lat = _make(case, tau)[0]
+    lat.step(k, history=False)
+    _check(lat, ref, f"{case} k={k} tau={tau}")
+    if tau == 0.5:
+        assert not lat.stress().any() and not lat.shear(wall_only=False)[0].any() and not lat.shear()[0].any()
     lat.close()
 
 
